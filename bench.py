@@ -13,7 +13,21 @@ on the gfx950 kernels → bucketed RCCL gradient all-reduce overlapped with back
 weight re-pack.  Weights are random-init (no network); data is synthetic uint8 frames of the Kinetics
 clip shape (64 source frames = 2.13 s at 30 fps, 256x340).  Timing: W untimed warmup steps (plus one
 untimed autotuning pass, in which the ranks agree on kernel configurations), then K steps bracketed by
-barrier + device synchronize, max over ranks; rank 0 prints one JSON line.
+barrier + device synchronize, max over ranks; rank 0 prints one JSON line.  ``ms_per_step`` is the wall time of the
+K timed steps divided by K.  A plain run does nothing beyond that; secondary measurements go behind ``--full``.
+
+``--dump-outputs DIR``: after the timed steps rank 0 writes what the last timed step returned — ``loss.npy``,
+``logits.npy`` [batch, classes] — and ``params.npy``, a fixed seeded sample of the flat parameters after that step,
+all float32 (17 MB at the defaults).  Model, data, augmentation parameters and dropout key are seeded, so the inputs
+are the same in every run with the same arguments.  What is computed from them repeats only on the
+bitwise-reproducible executor: the default one adds weight gradients with atomics in arrival order and sums split
+reductions in an order the autotuner picks, and the random-init network amplifies that rounding noise from step to
+step, up to several per cent in the logits after a dozen optimizer steps.  So that two runs, or two builds, can be
+compared array for array, ``--dump-outputs`` selects ``--deterministic 1`` unless the caller passes
+``--deterministic 0``; a note on stderr and ``config.deterministic`` in the result line say which executor ran.  The
+deterministic executor is slower (one stream, generic stems, built-in kernel choices), and ``value`` and
+``ms_per_step`` of such a run are that executor's: the headline figure comes from a run without this option.
+``--deterministic 0 --dump-outputs DIR`` times and dumps the default executor, with the run-to-run noise above.
 
 ``--plumbing``: CPU/gloo rehearsal of the same launch + gradient-sync path on the reference PyTorch
 modules (tiny crop, no dropout) — what the CPU test suite drives (tests/test_bench_launch_cpu.py).
@@ -75,9 +89,9 @@ def parse(argv=None):
     ap.add_argument("--dump", default=None,
                     help="write the first optimizer step's (all-reduced) flat gradient and every rank's final "
                          "parameters here (cross-rank numerics tests)")
-    ap.add_argument("--deterministic", action="store_true",
-                    help="bitwise-reproducible fused executor (fixed-order reductions, one stream; cross-rank exactness "
-                         "tests)")
+    ap.add_argument("--deterministic", type=int, choices=(0, 1), nargs="?", const=1, default=None,
+                    help="1 (or no value): bitwise-reproducible fused executor (fixed-order reductions, one stream; "
+                         "cross-rank exactness tests); 0: the default executor.  Default: 0, or 1 with --dump-outputs")
     ap.add_argument("--source", choices=("synthetic", "host"), default="synthetic",
                     help="synthetic: decoded uint8 clips resident on the device (preprocessing only); host: a raw-frame "
                          ".npy corpus read by the native C++ reader into pinned memory, H2D on a copy stream, then "
@@ -89,7 +103,22 @@ def parse(argv=None):
     ap.add_argument("--data-rank", type=int, default=-1,
                     help="draw the synthetic data of this rank instead of the own one (single-process oracle runs "
                          "of a multi-rank job's shards)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (loss, logits) and a fixed "
+                         "seeded sample of the parameters it left behind as DIR/<name>.npy, float32.  Selects "
+                         "--deterministic 1 unless --deterministic 0 is given (stderr and the result line say so): "
+                         "only that executor's outputs repeat from run to run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond its headline figure (secondary "
+                         "measurements belong here, never in a plain run; there are none at present)")
     a = ap.parse_args(argv)
+    if a.deterministic is None:
+        # dumped outputs repeat from run to run only on the bitwise-reproducible executor (module docstring)
+        a.deterministic = int(bool(a.dump_outputs))
+        if a.dump_outputs and not a.plumbing and int(os.environ.get("RANK", "0")) == 0:
+            print("bench.py: --dump-outputs runs the deterministic executor (slower; --deterministic 0 keeps the "
+                  "default one, whose outputs differ from run to run)", file=sys.stderr)
+    a.deterministic = bool(a.deterministic)
     if not a.batch:
         a.batch = 32 if a.precision == "fp32" else 160
     return a
@@ -189,6 +218,27 @@ def host_loader(a, st, eng, dev):
             yield b["video"], b["label"]
 
 
+# ---------------------------------------------------------------------------------------------- outputs
+OUTPUT_SAMPLE = 4 * 2 ** 20   # elements kept of an output larger than this (16 MiB as float32)
+
+
+def dump_outputs(root: str, arrays) -> None:
+    """``--dump-outputs``: every array as ``root/<name>.npy`` in float32.  An array of more than OUTPUT_SAMPLE
+    elements is reduced to that many distinct (flattened) elements, at sorted indices drawn from a fixed seed — the
+    same indices in every run and every build, so two dumps compare element for element."""
+    import numpy as np
+    os.makedirs(root, exist_ok=True)
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.detach()
+        if t.numel() > OUTPUT_SAMPLE:
+            g = torch.Generator().manual_seed(20240229)
+            idx = torch.randperm(t.numel(), generator=g)[:OUTPUT_SAMPLE].sort().values   # each element once
+            t = t.reshape(-1).index_select(0, idx.to(t.device))
+        np.save(os.path.join(root, name + ".npy"), t.float().cpu().numpy())
+
+
 # ---------------------------------------------------------------------------------------------- main
 def run(a):
     from pytorchvideo_accelerate_amd.parallel.dist import DistState
@@ -201,6 +251,7 @@ def run(a):
     gdt = torch.bfloat16 if a.grad_dtype == "bf16" else None
     B = a.batch
     dump = {}
+    kept = {}      # logits of the most recent micro-step (--dump-outputs)
     gstep = None   # engine.graph.GraphedStep when --graph 1 (single process)
     scaler = None
     skipped = [0]  # fp16: optimizer steps skipped by the loss scaler (overflow)
@@ -217,7 +268,7 @@ def run(a):
             opt.zero_grad()
             for j in range(a.grad_accum):
                 xs, y = plumbing_batch(a, st.rank, i * a.grad_accum + j)
-                loss, _ = be.train_step(xs, y, loss_scale=1.0 / a.grad_accum, sync=j == a.grad_accum - 1)
+                loss, kept["logits"] = be.train_step(xs, y, loss_scale=1.0 / a.grad_accum, sync=j == a.grad_accum - 1)
             if i == 0 and a.dump:
                 dump["grad"] = be.flat.grad.clone()
             opt.step()
@@ -260,7 +311,8 @@ def run(a):
                 k = i * a.grad_accum + j
                 last = j == a.grad_accum - 1
                 sync.begin(last and not tune)
-                loss, _ = eng.forward_backward(clips[k % 2], labels_all[k % 64], loss_scale=1.0 / a.grad_accum)
+                loss, kept["logits"] = eng.forward_backward(clips[k % 2], labels_all[k % 64],
+                                                            loss_scale=1.0 / a.grad_accum)
                 sync.finish()
             if tune:
                 return None
@@ -348,8 +400,8 @@ def run(a):
                     if j:
                         xs = batch(i * a.grad_accum + j)
                     last = j == a.grad_accum - 1
-                    loss, _ = gstep(xs, labels_all[(i * a.grad_accum + j) % 64], loss_scale=1.0 / a.grad_accum,
-                                    accumulate=j > 0, optimizer_step=last)
+                    loss, kept["logits"] = gstep(xs, labels_all[(i * a.grad_accum + j) % 64],
+                                                 loss_scale=1.0 / a.grad_accum, accumulate=j > 0, optimizer_step=last)
                 return loss
             if tune:
                 # untimed autotuning pass: every conv geometry is tuned (ranks agree on the choice) with
@@ -364,7 +416,8 @@ def run(a):
                     xs = batch(i * a.grad_accum + j)
                 last = j == a.grad_accum - 1
                 sync.begin(last)
-                loss, _ = eng.forward_backward(xs, labels_of(i * a.grad_accum + j), loss_scale=ls / a.grad_accum)
+                loss, kept["logits"] = eng.forward_backward(xs, labels_of(i * a.grad_accum + j),
+                                                            loss_scale=ls / a.grad_accum)
                 sync.finish()
             if i == 0 and a.dump:
                 dump["grad"] = eng.flat.grad.clone()
@@ -428,6 +481,8 @@ def run(a):
         if st.is_main_process:
             torch.save({"grad": dump["grad"].cpu(), "params": [g.cpu() for g in gathered],
                         "world_size": st.world_size}, a.dump)
+    if a.dump_outputs and st.is_main_process and a.steps:
+        dump_outputs(a.dump_outputs, {"loss": loss, "logits": kept.get("logits"), "params": opt.flat.data})
     if st.is_main_process:
         headline = ((a.model, a.depth, a.frames, a.crop, a.alpha) == ("slowfast", 50, 32, 224, 4)
                     and not a.plumbing)

@@ -54,8 +54,28 @@ def test_bench_self_launch_two_ranks(tmp_path):
 
 
 def test_bench_single_rank_plumbing(tmp_path):
-    res = _run(["--gpus", "1"], tmp_path)
+    import numpy as np
+    out = tmp_path / "outputs"
+    res = _run(["--gpus", "1", "--dump-outputs", str(out), "--full"], tmp_path)
     assert res["n_gpus"] == 1 and res["config"]["parallelism"] == "dp1"
+    assert res["steps"] == 1 and res["ms_per_step"] > 0
+    # --dump-outputs: what the last timed step returned, and the (sampled) parameters it left, as float32 .npy
+    got = {f: np.load(str(out / f)) for f in sorted(os.listdir(out))}
+    assert sorted(got) == ["logits.npy", "loss.npy", "params.npy"]
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())
+    assert got["logits.npy"].shape == (2, 5) and got["loss.npy"].size == 1
+    assert abs(float(got["loss.npy"]) - res["config"]["final_loss"]) < 1e-3
+    import bench
+    assert got["params.npy"].shape == (bench.OUTPUT_SAMPLE,)
+    # dumped outputs must repeat run to run: the option selects the bitwise-reproducible executor unless the
+    # caller chooses; an explicit choice, either way, is kept
+    assert res["config"]["deterministic"] is True
+    assert bench.parse(["--dump-outputs", "x"]).deterministic is True
+    assert bench.parse(["--dump-outputs", "x", "--deterministic", "0"]).deterministic is False
+    assert bench.parse(["--deterministic", "--batch", "4"]).deterministic is True
+    assert bench.parse(["--deterministic", "1"]).deterministic is True
+    assert bench.parse([]).deterministic is False
+    assert sum(v.nbytes for v in got.values()) <= 64 * 2 ** 20
 
 
 def test_forced_gradsync_single_rank_gloo(tmp_path):
@@ -72,14 +92,19 @@ def test_forced_gradsync_single_rank_gloo(tmp_path):
     d1 = str(tmp_path / "forced.pt")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
                         "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(REPO, "bench.py"),
-                        "--gpus", "1", "--dump", d1] + ARGS, capture_output=True, text=True, timeout=900,
+                        "--gpus", "1", "--dump", d1, "--dump-outputs", str(tmp_path / "o1")] + ARGS,
+                       capture_output=True, text=True, timeout=900,
                        cwd=str(tmp_path), env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert res["config"]["backend"] == "gloo" and res["config"]["forced_sync"] is True
     d0 = str(tmp_path / "plain.pt")
-    res0 = _run(["--gpus", "1", "--dump", d0], tmp_path)
+    res0 = _run(["--gpus", "1", "--dump", d0, "--dump-outputs", str(tmp_path / "o0")], tmp_path)
     assert res0["config"]["backend"] == "none"
     g1 = torch.load(d1, weights_only=True)["grad"]
     g0 = torch.load(d0, weights_only=True)["grad"]
     assert torch.equal(g0, g1)
+    # same arguments, same inputs: the two processes' --dump-outputs agree array for array
+    import numpy as np
+    for f in ("loss.npy", "logits.npy", "params.npy"):
+        assert np.array_equal(np.load(str(tmp_path / "o0" / f)), np.load(str(tmp_path / "o1" / f))), f

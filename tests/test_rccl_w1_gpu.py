@@ -10,6 +10,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -72,9 +73,46 @@ def test_rccl_forced_gradsync_bench_matches_unsynced(tmp_path, comm):
         assert k in cfg and math.isfinite(cfg[k]), cfg
     assert cfg["buckets"] > 1
     d0 = str(tmp_path / "plain.pt")
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + BENCH + ["--dump", d0],
+    out = tmp_path / "outputs"
+    # the un-synced run leaves the executor to --dump-outputs, which selects the deterministic one (else the bitwise
+    # comparison with the explicit --deterministic run above fails)
+    plain = [x for x in BENCH if x != "--deterministic"] + ["--dump", d0, "--dump-outputs", str(out)]
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + plain,
                        capture_output=True, text=True, timeout=400, cwd=str(tmp_path), env=_env())
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     g1 = torch.load(d1, weights_only=True)["grad"]
     g0 = torch.load(d0, weights_only=True)["grad"]
     assert torch.equal(g0, g1), float((g0 - g1).abs().max())
+    # --dump-outputs: the last timed step's loss and logits, a sample of the parameters it left
+    res0 = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert res0["config"]["deterministic"] is True and "deterministic executor" in r.stderr
+    got = _check_dump(out, res0)
+    # the same arguments in another process (the other ``comm`` case) wrote the same arrays, bit for bit
+    for f, v in _DUMPS.setdefault("plain", got).items():
+        assert np.array_equal(v, got[f]), f
+
+
+_DUMPS = {}
+
+
+def _check_dump(out, res):
+    got = {f: np.load(str(out / f)) for f in sorted(os.listdir(out))}
+    assert sorted(got) == ["logits.npy", "loss.npy", "params.npy"]
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())
+    assert got["logits.npy"].shape == (4, 400) and got["params.npy"].shape == (4 * 2 ** 20,)
+    assert abs(float(got["loss.npy"]) - res["config"]["final_loss"]) < 1e-3
+    assert res["steps"] == 2 and res["ms_per_step"] > 0
+    return got
+
+
+def test_dump_outputs_of_the_default_executor(tmp_path):
+    """``--deterministic 0 --dump-outputs``: the caller's choice holds and the default executor (both pathway streams,
+    s2d stems, atomic weight gradients; built-in kernel choices here, to keep the test short) is timed and dumped."""
+    out = tmp_path / "outputs"
+    args = [x for x in BENCH if x != "--deterministic"] + ["--deterministic", "0", "--dump-outputs", str(out)]
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + args, capture_output=True, text=True,
+                       timeout=400, cwd=str(tmp_path), env=_env(PVA_ARMS="autotune=0"))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert res["config"]["deterministic"] is False and "deterministic executor" not in r.stderr
+    _check_dump(out, res)
